@@ -6,7 +6,8 @@
 
 One step = videocad_amd.trainer.BaseTrainer.train_step (what _process_batch calls) on one synthetic loader-shaped batch resident in HBM:
 forward -> fused loss -> backward -> (gradient all-reduce over RCCL, overlapped, N > 1) -> clip(1.0) -> Adam.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0 (`ms_per_step` = wall time of the K timed steps / K).  `--dump-outputs DIR` also writes what the last timed step
+computed as .npy files; the inputs (synthetic batch, hash-init weights, dropout seeds) depend only on the arguments.
 """
 import argparse
 import json
@@ -44,7 +45,11 @@ def main(argv=None):
     ap.add_argument("--grad-wire", default="fp32", choices=["fp32", "half"], help="N > 1: gradient buckets on the wire in fp32 (reference) or in the library's 16-bit storage format")
     ap.add_argument("--grad-exchange", default="all_reduce", choices=["all_reduce", "rs_ag", "auto"], help="N > 1: one all_reduce per bucket, or reduce_scatter + all_gather (auto: buckets >= 32 MB)")
     ap.add_argument("--profile-only", action="store_true", help="rocprofv3 runs: only the headline workload's train steps (no seq-186 / PCIe / parity / CPU-baseline legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (loss, metric counters, a fixed sample of the "
+                                                             "updated parameters) as DIR/<name>.npy, to compare two builds output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.profile_only:
         args.no_cpu_baseline = args.no_seq186 = args.no_pcie = args.no_parity = args.no_modes = True
 

@@ -158,8 +158,9 @@ def logit_parity(model, device):
 
 
 def _timed(tr, bd, steps, world, device, per_step=None):
-    """K steps between barrier + synchronize on both sides (wall clock = the reported time); `per_step` (a list) additionally receives
-    the K step durations in ms from events recorded on the compute stream inside the same region (no extra synchronisation)."""
+    """K steps between barrier + synchronize on both sides (wall clock = the reported time) -> (seconds, loss and metric counters of the last
+    step); `per_step` (a list) additionally receives the K step durations in ms from events recorded on the compute stream inside the same
+    region (no extra synchronisation)."""
     import torch.distributed as dist
     torch.cuda.synchronize()
     if world > 1:
@@ -184,7 +185,28 @@ def _timed(tr, bd, steps, world, device, per_step=None):
         elapsed = float(tt.item())
     if evs:
         per_step.extend(evs[i].elapsed_time(evs[i + 1]) for i in range(steps))
-    return elapsed, loss
+    return elapsed, loss, met
+
+
+DUMP_PARAM_DRAWS = 1 << 22      # --dump-outputs: ~4 M sampled parameter values (16 MB) of the canonical model's 127 M
+
+
+def dump_outputs(path, eng, loss, met):
+    """`bench.py --dump-outputs DIR`: what the last timed `train_step` computed, as float arrays — loss.npy (the loss it returned), metrics.npy (the
+    int32 metric counters it returned, exact in float64) and params.npy (the updated fp32 parameters at a fixed sample of positions: seed-0 draws over
+    the parameters concatenated in name order, so the positions do not depend on the library's buffer layout)."""
+    os.makedirs(path, exist_ok=True)
+    names = sorted(eng.table)
+    offs = np.array([eng.table[n][0] for n in names], dtype=np.int64)
+    sizes = np.array([eng.table[n][1] for n in names], dtype=np.int64)
+    starts = np.cumsum(sizes) - sizes
+    pos = np.unique(np.random.default_rng(0).integers(0, int(sizes.sum()), size=DUMP_PARAM_DRAWS))
+    which = np.searchsorted(starts, pos, side="right") - 1
+    phys = torch.from_numpy(offs[which] + (pos - starts[which])).to(eng.params.device)
+    arrays = {"loss": loss.detach().float().cpu().numpy(), "metrics": met.cpu().numpy().astype(np.float64),
+              "params": eng.params[phys].float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def short_leg(dtype, fp8, B, T, steps, warmup, device, rank, world, seed, dropout, want_parity=True):
@@ -198,7 +220,7 @@ def short_leg(dtype, fp8, B, T, steps, warmup, device, rank, world, seed, dropou
     for _ in range(warmup):
         tr.train_step(bd)
     per = []
-    e, loss = _timed(tr, bd, steps, world, device, per)
+    e, loss, _ = _timed(tr, bd, steps, world, device, per)
     out = {"workload": f"seq_len={T} batch={B} per GPU", "dtype": dtype + ("+fp8 forward GEMMs (ViT)" if fp8 else ""),
            "value": round(world * B * T / (e / steps), 1), "unit": "frames/s", "ms_per_step": round(e / steps * 1e3, 3),
            "ms_per_step_median": round(float(np.median(per)), 3), "steps": steps, "warmup": warmup, "loss": float(loss.item())}
@@ -320,14 +342,16 @@ def run(args):
     for _ in range(args.warmup):
         tr.train_step(bd)
     per_step_ms = []
-    elapsed, loss = _timed(tr, bd, args.steps, world, device, per_step_ms)
+    elapsed, loss, met = _timed(tr, bd, args.steps, world, device, per_step_ms)
+    if rank == 0 and getattr(args, "dump_outputs", None):      # before any later step moves the parameters
+        dump_outputs(args.dump_outputs, eng, loss, met)
     ms = elapsed / args.steps * 1e3
     fps = world * B * T / (elapsed / args.steps)
 
     comm = None
     if world > 1:        # exposed communication: the same steps with the all-reduces skipped (diagnostic, outside the timed region)
         tr.gradsync.skip_comm = True
-        e_nc, _ = _timed(tr, bd, max(3, args.steps // 2), world, device)
+        e_nc, _, _ = _timed(tr, bd, max(3, args.steps // 2), world, device)
         tr.gradsync.skip_comm = False
         ms_nc = e_nc / max(3, args.steps // 2) * 1e3
         comm = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(), "buckets": len(eng.buckets),
@@ -356,7 +380,7 @@ def run(args):
             for _ in range(W2):
                 tr.train_step(bd2)
             per2 = []
-            e2, _ = _timed(tr, bd2, K2, world, device, per2)
+            e2, _, _ = _timed(tr, bd2, K2, world, device, per2)
             leg = {"workload": f"seq_len={T2} batch={B2} per GPU (BASELINE configs[{3 if name == 'c4' else 2}]" + (" per-GPU shape)" if name == "c4" else ")"),
                    "value": round(world * B2 * T2 / (e2 / K2), 1), "unit": "frames/s", "ms_per_step": round(e2 / K2 * 1e3, 3),
                    "ms_per_step_median": round(float(np.median(per2)), 3), "steps": K2, "warmup": W2}
