@@ -209,6 +209,19 @@ int vcad_optimizer_step_groups(vcad_engine* e, const float* lr_per_bucket, float
  *   vcad_infer_step  : steps t = 0, 1, ... in order; frame = frame t of every clip (clip b at frame + b*frame_bstride, same pixel
  *                      type as begin), action_norm fp32 [B,7] = the (normalised) action fed at position t (zeros, or the masked
  *                      arg-max of step t-1, reference :249-263); cmds_out fp32 [B,5], params_out fp32 [B,6000] = logits of step t */
+/* ---- interpretability maps (reference trainer.py generate_saliency_batch / compute_attention_rollout)
+ * vcad_set_input_grads: arms the NEXT vcad_backward (or the next run of the staged backward's tower stages) to also write the pixel gradients of the
+ *   forward's fp32 inputs: dframes fp32 [B][T][S][S] contiguous (frame tower), dcad fp32 [B (1 + V)][S][S] (CAD tower: the B CAD images, then the
+ *   B x V multiview images — the order the tower sees them).  Either may be NULL; 16-byte aligned.  The backward clears it (so does any forward).
+ *   Refused after a uint8 / RGB8 forward, or with dframes when the wiring does not run the frame tower (enable_past_states = 0: the frames do not
+ *   reach the outputs).  Gradients are true ones (divided by the fp16 gradient scale).  Not armed: the backward launches exactly what it did before.
+ * vcad_cad_attention_rollout: eval-mode forward of the CAD tower over cad fp32 [B,1,S,S] (the (B, T = 1) plan: the workspace must hold
+ *   vcad_rollout_workspace_bytes(B); it replaces the training activations) and the attention rollout of its layers:
+ *   A_l = mean_heads(softmax_l) + I, row-normalised;  out fp32 [B][P] = row 0 of A_L ... A_1, patch tokens 1 .. P. */
+int vcad_set_input_grads(vcad_engine* e, float* dframes, float* dcad);
+size_t vcad_rollout_workspace_bytes(const vcad_engine* e, int B);
+int vcad_cad_attention_rollout(vcad_engine* e, const float* cad, int B, float* out, void* stream);
+
 size_t vcad_infer_workspace_bytes(const vcad_engine* e, int B, int Tmax);
 int vcad_infer_begin(vcad_engine* e, const float* cad, int B, int Tmax, void* stream);
 int vcad_infer_begin_u8(vcad_engine* e, const uint8_t* cad, int B, int Tmax, void* stream);
@@ -313,6 +326,17 @@ int vcad_op_attention_bwd(int t, int D, const void* q, const void* k, const void
 int vcad_op_cls_attention_fwd(const void* ha, int64_t ld_ha, const void* g, void* c, float* lse, int N, int H, int P1, float scale, void* stream);
 int vcad_op_cls_attention_bwd(const void* ha, int64_t ld_ha, const void* g, const void* dc, const float* lse, void* dg, void* dha, int64_t ld_dha,
                               float* r0, int N, int H, int P1, float scale, void* stream);
+/* interpretability kernels (csrc/interp.h; the engine's vcad_set_input_grads / vcad_cad_attention_rollout launch them):
+ * patch_grad: pixel gradient of Rearrange -> LayerNorm(1024) from dxh [rows][1024] (td: 0 fp32, 1 16-bit) = the normalised patches' gradient, or the
+ *   LayerNorm output's gradient when gamma is given; x fp32 pixels (image n = b T + t at x + b ldx + t S^2), stats [rows][2] (mean, rstd); out fp32 in
+ *   image layout (image n at out + b ldo + t S^2), multiplied by inv_scale.
+ * attention_rollout: qkv[l] [N P1][3 H 64] (st: 0 fp32, 1 16-bit, 2 bf16x3 pre-split words), lse[l] [N][H][P1] for the nfull full layers; the last
+ *   (class-token) layer from last_qkv (q at each image's class row, keys of all tokens; last_st 0 / 1) or, cls = 1, from ha [N P1][D] and g [N][H][D]
+ *   (16-bit); last_lse [N][H].  out fp32 [N][P1 - 1]. */
+int vcad_op_patch_grad(int td, const void* dxh, const float* gamma, const float* x, int64_t ldx, const float* stats, float* out, int64_t ldo,
+                       int64_t rows, int img, int patch, int T, float inv_scale, void* stream);
+int vcad_op_attention_rollout(int st, const void* const* qkv, const float* const* lse, int nfull, int cls, const void* last_qkv, int last_st,
+                              const float* last_lse, const void* ha, const void* g, int N, int H, int P1, int D, float scale, float* out, void* stream);
 /* same, with the saved forward output o passed along (the kernels recompute D_i from P and dP; o is accepted for callers that hold it) */
 int vcad_op_attention_bwd_o(int t, int D, const void* q, const void* k, const void* v, const void* o, int64_t ldo, const void* dout,
                             int64_t ldq, int64_t ldk, int64_t ldv, int64_t lddo, const float* lse, float* delta, void* dq, void* dk,

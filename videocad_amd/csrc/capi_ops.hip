@@ -143,4 +143,26 @@ int vcad_op_cls_attention_bwd(const void* ha, int64_t ld_ha, const void* g, cons
     return rc;
 }
 
+int vcad_op_patch_grad(int td, const void* dxh, const float* gamma, const float* x, int64_t ldx, const float* stats, float* out, int64_t ldo,
+                       int64_t rows, int img, int patch, int T, float inv_scale, void* stream) {
+    PatchGradParams p; memset(&p, 0, sizeof(p));
+    p.dxh = dxh; p.lddxh = (long)patch * patch; p.gamma = gamma; p.x = x; p.ldx = ldx; p.stats = stats; p.out = out; p.ldo = ldo;
+    p.rows = rows; p.img = img; p.patch = patch; p.T = T; p.inv_scale = inv_scale;
+    int rc = vc_patch_grad(td, p, (vc_stream_t)stream);
+    if (!rc && vc_last_launch_error()) { vc_set_error("vcad_op_patch_grad: launch failed"); return VC_ERR_LAUNCH; }
+    return rc;
+}
+
+int vcad_op_attention_rollout(int st, const void* const* qkv, const float* const* lse, int nfull, int cls, const void* last_qkv, int last_st,
+                              const float* last_lse, const void* ha, const void* g, int N, int H, int P1, int D, float scale, float* out, void* stream) {
+    if (nfull < 0 || nfull > RO_MAXL) { vc_set_error("vcad_op_attention_rollout: %d full layers (at most %d)", nfull, RO_MAXL); return VC_ERR_ARG; }
+    RolloutParams p; memset(&p, 0, sizeof(p));
+    for (int l = 0; l < nfull; ++l) { p.qkv[l] = qkv[l]; p.lse[l] = lse[l]; }
+    p.nfull = nfull; p.st = st; p.H = H; p.P1 = P1; p.inner = H * RO_DH; p.ldqkv = 3L * p.inner; p.scale = scale;
+    p.cls = cls; p.last_qkv = last_qkv; p.last_st = last_st; p.last_lse = last_lse; p.ha = ha; p.ldha = D; p.g = g; p.D = D; p.out = out;
+    int rc = vc_attn_rollout(p, N, (vc_stream_t)stream);
+    if (!rc && vc_last_launch_error()) { vc_set_error("vcad_op_attention_rollout: launch failed"); return VC_ERR_LAUNCH; }
+    return rc;
+}
+
 }  // extern "C"

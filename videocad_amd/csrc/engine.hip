@@ -124,6 +124,9 @@ struct vcad_engine {
     // Linear consumes (and its bias gradient), as every layer boundary inside a stage does — the stage boundary used to cost a dropout pass + a column sum
     bool du_carry = false; Mat du_carry_mat{nullptr, 0, 0};
     bool pe_fresh[2] = {false, false};       // folded patch-embedding weights (VitActs::pe_wf / pe_bf) match the parameters
+    // vcad_set_input_grads: pixel-gradient destinations of the NEXT backward, per tower ([0] frames [B][T][S][S], [1] the CAD tower's [B (1 + V)][S][S]); the tower's
+    // embedding backward consumes its pointer, every forward and the end of vcad_backward clear both.  Null (the training path): nothing is launched.
+    float* ig[2] = {nullptr, nullptr};
     // VCAD_FP8 forward mode (vcad_set_fp8): the four Linears of every full ViT layer run on the block-scaled fp8 matrix cores (gemm_mx8.h):
     // weights quantised from the fp32 master once per optimiser step (q8w / q8ws mirror the flat parameter layout: byte i <-> parameter i,
     // scale byte i/32), activations quantised into the lane's q8a / q8as right before each GEMM.  Backward is the bf16 path, unchanged.
@@ -898,6 +901,8 @@ int vit_backward(const Ctx& cx, int v, const float* de, int part /*0 = whole, 1 
             CK(cx.lin_wgrad(dpe, cx.AT(a.pn, pd), a.t_dwf, pd, cx.Gf(w.peb), (int)Rp, D, pd));
             if (w.ln1b != w.ln1w + pd) { vc_set_error("internal: patch-embedding LayerNorm weight / bias not adjacent"); return VC_ERR_ARG; }
             CK(vc_pe_fold_bwd(a.t_dwf, cx.Gf(w.peb), cx.Pf(w.pew), cx.Pf(w.ln1w), cx.Pf(w.ln1b), cx.Gf(w.pew), cx.Gf(w.ln1w), D, pd, cx.L().scr_lnpart, cx.L().scr_colsum, cx.s));
+            // armed (vcad_set_input_grads): the gradient of the normalised patches is one dgrad through the folded weight, dpe 16-bit(W diag gamma)
+            if (e->ig[v]) CK(cx.lin_dgrad(dpe, cx.AT(a.pe_wf, pd), cx.AT(cx.L().t_dpn, pd), (int)Rp, D, pd, Epi()));
         } else {
         CK(cx.lin_wgrad(dpe, cx.AT(a.pn, pd), cx.Gf(w.pew), pd, cx.Gf(w.peb), (int)Rp, D, pd));
         CK(cx.lin_dgrad(dpe, cx.W(w.pew, pd), cx.AT(cx.L().t_dpn, pd), (int)Rp, D, pd, Epi()));
@@ -907,6 +912,14 @@ int vit_backward(const Ctx& cx, int v, const float* de, int part /*0 = whole, 1 
             p.img = c.image_size; p.patch = c.patch_size; p.P = (int)img_T; p.u8 = v == 1 && e->in_u8 ? 1 : e->in_u8;
             CK(vc_ln_bwd(e->dt, VC_F32, e->dt, pd, 1, p, cx.L().scr_lnpart, cx.Gf(w.ln1w), cx.Gf(w.ln1b), cx.L().scr_colsum, cx.s));
         }
+        }
+        if (e->ig[v]) {      // pixel gradient (interp.h patch_grad_kernel): t_dpn is the LayerNorm output's gradient (x gamma here) or, folded, already the normalised patches'
+            PatchGradParams gp; memset(&gp, 0, sizeof(gp));
+            gp.dxh = cx.L().t_dpn; gp.lddxh = pd; gp.gamma = a.pe_fold ? nullptr : cx.Pf(w.ln1w);
+            gp.x = (const float*)img; gp.ldx = img_bstride; gp.stats = a.pstat; gp.out = e->ig[v]; gp.ldo = img_T * (long)c.image_size * c.image_size;
+            gp.rows = Rp; gp.img = c.image_size; gp.patch = c.patch_size; gp.T = (int)img_T; gp.inv_scale = 1.0f / e->grad_scale;
+            CK(vc_patch_grad(e->dt, gp, cx.s));
+            e->ig[v] = nullptr;
         }
     }
     return 0;
@@ -1446,6 +1459,7 @@ static int forward_any(vcad_engine* e, const void* frames, int64_t fbstride, con
         e->planned_ws = e->ws; e->infer_T = 0;
     }
     e->B = B; e->T = T; e->in_frames = frames; e->in_fbstride = fbstride; e->in_actions = actions; e->in_cad = cad; e->in_u8 = u8;
+    e->ig[0] = e->ig[1] = nullptr;
     e->fwd_valid = false; e->dls_valid = false;
     int rc = engine_forward(e, cmds_out, pars_out, (vc_stream_t)stream);
     if (rc) return rc;
@@ -1596,6 +1610,16 @@ int vcad_backward(vcad_engine* e, const float* dcmds, const float* dpars, void* 
     if (fork) CK(vc_event_record(e->ev_join, e->side));
     for (int st = CAD_STAGE + 1 + (frame_first ? 1 : 0); st < NB_BUCKETS; ++st) { CK(vcad_backward_stage(e, st, dcmds, dpars, stream)); CK(ready(st, s)); }
     if (fork) CK(vc_stream_wait_event(s, e->ev_join));
+    e->ig[0] = e->ig[1] = nullptr;
+    return 0;
+}
+
+int vcad_set_input_grads(vcad_engine* e, float* dframes, float* dcad) {
+    if (!e->fwd_valid) { vc_set_error("vcad_set_input_grads: no forward activations (call vcad_forward first)"); return VC_ERR_ARG; }
+    if ((dframes || dcad) && e->in_u8) { vc_set_error("vcad_set_input_grads: the forward read uint8 pixels (vcad_forward_u8 / _rgb8): no pixel gradient"); return VC_ERR_UNSUPPORTED; }
+    if (dframes && !e->c.enable_past_states) { vc_set_error("vcad_set_input_grads: this wiring does not run the frame tower (enable_past_states = 0): the frames take no gradient"); return VC_ERR_ARG; }
+    if (((uintptr_t)dframes | (uintptr_t)dcad) & 15) { vc_set_error("vcad_set_input_grads: gradient buffers must be 16-byte aligned"); return VC_ERR_ARG; }
+    e->ig[0] = dframes; e->ig[1] = dcad;
     return 0;
 }
 
@@ -1657,6 +1681,48 @@ int vcad_infer_begin(vcad_engine* e, const float* cad, int B, int Tmax, void* st
 int vcad_infer_begin_u8(vcad_engine* e, const uint8_t* cad, int B, int Tmax, void* stream) {
     if ((uintptr_t)cad & 3) { vc_set_error("vcad_infer_begin_u8: cad must be 4-byte aligned"); return VC_ERR_ARG; }
     return infer_begin_any(e, cad, 1, B, Tmax, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Attention rollout of the CAD tower (reference trainer.py compute_attention_rollout): the (B, T = 1) plan, an eval-mode forward of the CAD tower over
+// the B CAD images, then one workgroup per image recomputes every layer's head-averaged attention from the saved qkv / lse (interp.h attn_rollout_kernel).
+// ---------------------------------------------------------------------------------------------------------------
+size_t vcad_rollout_workspace_bytes(const vcad_engine* e, int B) {
+    vcad_engine tmp = *e;
+    return plan(&tmp, B, 1, nullptr);
+}
+int vcad_cad_attention_rollout(vcad_engine* e, const float* cad, int B, float* out, void* stream) {
+    if (!e->P) { vc_set_error("vcad_cad_attention_rollout: parameters not bound"); return VC_ERR_ARG; }
+    CK(need_device(e, "vcad_cad_attention_rollout"));
+    const vcad_config& c = e->c;
+    if (B < 1 || !cad || !out) { vc_set_error("vcad_cad_attention_rollout: bad B=%d or null pointer", B); return VC_ERR_ARG; }
+    if (c.vit_dim_head != RO_DH || c.vit_heads > RO_MAXH || c.vit_depth - 1 > RO_MAXL) { vc_set_error("vcad_cad_attention_rollout: ViT heads %d x %d / depth %d unsupported", c.vit_heads, c.vit_dim_head, c.vit_depth); return VC_ERR_UNSUPPORTED; }
+    if (!e->ws) { vc_set_error("vcad_cad_attention_rollout: no workspace"); return VC_ERR_WORKSPACE; }
+    { vcad_engine tmp = *e; const size_t need = plan(&tmp, B, 1, nullptr);
+      if (need > e->ws_bytes) { vc_set_error("vcad_cad_attention_rollout: workspace %zu < %zu bytes", e->ws_bytes, need); return VC_ERR_WORKSPACE; } }
+    plan(e, B, 1, e->ws);
+    // (the tower runs over the B CAD images only, not a multiview engine's B (1 + V): the next forward re-plans)
+    e->B = B; e->T = 1; e->planned_ws = nullptr; e->fwd_valid = false; e->infer_T = 0; e->in_u8 = 0; e->in_cad = cad; e->ig[0] = e->ig[1] = nullptr;
+    VitActs& a = e->va[1]; a.N = B;
+    const float keep_p = e->drop_p; e->drop_p = 0.f;        // model.eval()
+    vc_stream_t s = (vc_stream_t)stream; Ctx cx{e, s};
+    int rc = cx.refresh_q8();
+    for (int ln = 0; ln < 2 && !rc; ++ln) rc = vc_memset_async(e->lane[ln].claim, 0, 64 * sizeof(int), s);     // (see infer_begin_any)
+    if (!rc) rc = vit_forward(cx, 1, cad, 1, (long)c.image_size * c.image_size);
+    e->drop_p = keep_p;
+    if (rc) return rc;
+    const int g = c.image_size / c.patch_size, P1 = g * g + 1, inner = c.vit_heads * c.vit_dim_head, depth = c.vit_depth;
+    RolloutParams rp; memset(&rp, 0, sizeof(rp));
+    rp.nfull = depth - 1;
+    for (int L = 0; L < depth - 1; ++L) { rp.qkv[L] = a.L[L].qkv; rp.lse[L] = a.L[L].lse; }
+    rp.st = cx.pk_acts() ? 2 : (e->dt == VC_BF16 ? 1 : 0);
+    rp.ldqkv = 3L * inner; rp.H = c.vit_heads; rp.P1 = P1; rp.inner = inner; rp.scale = 1.0f / sqrtf((float)c.vit_dim_head);
+    const VitLayerActs& last = a.L[depth - 1];
+    rp.cls = e->cls[1].on ? 1 : 0; rp.last_qkv = last.qkv; rp.last_st = e->dt == VC_BF16 ? 1 : 0; rp.last_lse = last.lse;
+    rp.ha = last.h_a; rp.ldha = c.vit_dim; rp.g = e->cls[1].g; rp.D = c.vit_dim; rp.out = out;
+    CK(vc_attn_rollout(rp, B, s));
+    if (vc_last_launch_error()) { vc_set_error("vcad_cad_attention_rollout: kernel launch failed"); return VC_ERR_LAUNCH; }
+    return 0;
 }
 
 // one cached attention: the single query row of step t against rows [lo(t) .. t] of this layer's cache

@@ -115,6 +115,29 @@ bool vc_cls_attn_ok(int D, int H, int P1, int dim_head);
 int vc_cls_attn_fwd(ClsAttnParams p, vc_stream_t s);
 int vc_cls_attn_bwd(ClsAttnParams p, vc_stream_t s);
 
+// interpretability maps (interp.h; never on the training path): td = VC_F32 | VC_BF16 (type of dxh)
+struct PatchGradParams {
+    const void* dxh; long lddxh;      // [rows][1024] (type TD)
+    const float* gamma;               // optional [1024]
+    const float* x; long ldx;         // fp32 pixels; image n = b T + t at x + b ldx + t img^2 (the forward's batch stride)
+    const float* stats;               // [rows][2] = mean, rstd (the forward's)
+    float* out; long ldo;             // fp32 pixel gradient, image n at out + b ldo + t img^2
+    long rows; int img, patch, T; float inv_scale;
+};
+constexpr int RO_MAXP = 64, RO_LD = RO_MAXP + 1, RO_MAXL = 16, RO_MAXH = 16, RO_DH = 64;
+struct RolloutParams {
+    const void* qkv[RO_MAXL]; const float* lse[RO_MAXL];      // layers 0 .. nfull - 1 (full attention)
+    int nfull; int st;                                          // st: storage of those qkv — 0 fp32, 1 16-bit, 2 pre-split bf16x3 words
+    long ldqkv; int H, P1, inner; float scale;
+    // the last layer: cls = 0 -> q at the class row of last_qkv (type last_st: 0 fp32, 1 16-bit), keys at column inner of every row; lse [N][H]
+    //                 cls = 1 -> ha [N P1][D] normalised tokens and g [N][H][D] (16-bit), lse [N][H]
+    int cls; const void* last_qkv; int last_st; const float* last_lse;
+    const void* ha; long ldha; const void* g; int D;
+    float* out;                                                 // [N][P1 - 1]
+};
+int vc_patch_grad(int td, PatchGradParams p, vc_stream_t s);
+int vc_attn_rollout(RolloutParams p, long N, vc_stream_t s);
+
 int vc_loss_fwd(LossParams p, vc_stream_t s);          // rows + finalize
 int vc_loss_bwd(LossParams p, vc_stream_t s);          // dlogits
 

@@ -305,3 +305,27 @@ int vc_adam(AdamParams a, vc_stream_t s) {
     VC_LAUNCH(adam_kernel, dim3((unsigned)nb), dim3(256), 0, s, a);
     return VC_OK;
 }
+
+// ---- interpretability maps (interp.h): pixel gradient of the patch embedding, attention rollout of a ViT tower
+#include "interp.h"
+int vc_patch_grad(int td, PatchGradParams p, vc_stream_t s) {
+    if (p.rows <= 0) return VC_OK;
+    if (p.patch * p.patch != 1024 || p.img % p.patch || p.T < 1 || (p.ldx & 3) || (p.ldo & 3) || (p.img & 3)) {
+        vc_set_error("patch_grad: patch %d / image %d / strides unsupported (1024-wide patches, 16-byte aligned rows)", p.patch, p.img); return VC_ERR_UNSUPPORTED;
+    }
+    ProfScope ps(VC_CAT_NORM, 0, (double)p.rows * 1024 * ((td == VC_BF16 ? 2 : 4) + 8), s);
+    const dim3 grid((unsigned)VC_CEIL_DIV(p.rows, 4));
+    if (td == VC_F32) VC_LAUNCH((patch_grad_kernel<float, 16>), grid, dim3(256), 0, s, p);
+    else if (td == VC_BF16) VC_LAUNCH((patch_grad_kernel<vc_bf16, 16>), grid, dim3(256), 0, s, p);
+    else { vc_set_error("patch_grad: dtype %d", td); return VC_ERR_UNSUPPORTED; }
+    return VC_OK;
+}
+int vc_attn_rollout(RolloutParams p, long N, vc_stream_t s) {
+    if (N <= 0) return VC_OK;
+    if (p.P1 < 2 || p.P1 > RO_MAXP || p.H < 1 || p.H > RO_MAXH || p.nfull < 0 || p.nfull > RO_MAXL || p.inner != p.H * RO_DH || (p.cls && (long)p.H * p.D > 2L * RO_MAXP * RO_LD)) {
+        vc_set_error("attn_rollout: P1=%d H=%d layers=%d inner=%d unsupported (P1 <= %d, H <= %d, 64-wide heads)", p.P1, p.H, p.nfull + 1, p.inner, RO_MAXP, RO_MAXH); return VC_ERR_UNSUPPORTED;
+    }
+    ProfScope ps(VC_CAT_ATTN, 2.0 * N * (p.nfull * ((double)p.H * p.P1 * p.P1 * RO_DH + (double)p.P1 * p.P1 * p.P1)), (double)N * p.nfull * p.P1 * p.ldqkv * 2, s);
+    VC_LAUNCH(attn_rollout_kernel, dim3((unsigned)N), dim3(256), 0, s, p);
+    return VC_OK;
+}

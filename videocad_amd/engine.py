@@ -246,6 +246,35 @@ class NativeEngine:
         L.check(self.lib, fn(self.h, _ptr(cad), B, Tmax, self.stream()), "infer_begin")
         self._infer_u8 = u8
 
+    # ------------------------------------------------------------------ interpretability maps (include/vcad.h: vcad_set_input_grads / vcad_cad_attention_rollout)
+    def set_input_grads(self, dframes: Optional[torch.Tensor] = None, dcad: Optional[torch.Tensor] = None):
+        """arm the NEXT backward to also write the pixel gradients of the current forward's fp32 inputs: dframes fp32 [B,T,S,S] contiguous, dcad fp32
+        [B (1 + V), S, S] contiguous (the B CAD images, then the B x V multiview images).  Either may be None; the backward clears the arming."""
+        S = self.cfg.image_size
+        for t in (dframes, dcad):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.device == self.device and t.numel() % (S * S) == 0)
+        self._keep_g = (dframes, dcad)
+        L.check(self.lib, self.lib.vcad_set_input_grads(self.h, _ptr(dframes), _ptr(dcad)), "set_input_grads")
+
+    def attention_rollout(self, cad: torch.Tensor) -> torch.Tensor:
+        """cad fp32 [B,1,S,S] (normalised pixels) -> [B, P]: the CAD tower's attention rollout, class token to the P patches (eval mode; replaces the
+        engine's activations like infer_begin does)"""
+        S = self.cfg.image_size
+        assert cad.dtype == torch.float32 and cad.numel() % (S * S) == 0, (cad.dtype, tuple(cad.shape))
+        B = cad.numel() // (S * S)
+        need = max(int(self.lib.vcad_rollout_workspace_bytes(self.h, B)), self.ws.numel() if self.ws is not None else 0)
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = None
+            self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            L.check(self.lib, self.lib.vcad_set_workspace(self.h, _ptr(self.ws), need), "set_workspace")
+        cad = cad.contiguous()
+        g = S // self.cfg.patch_size
+        out = torch.empty(B, g * g, device=self.device)
+        self._keep_r = cad
+        self.fwd_serial += 1                                 # the (B, 1) plan replaces the training activations
+        L.check(self.lib, self.lib.vcad_cad_attention_rollout(self.h, _ptr(cad), B, _ptr(out), self.stream()), "cad_attention_rollout")
+        return out
+
     def infer_step(self, t: int, frame: Optional[torch.Tensor], action_norm: Optional[torch.Tensor]):
         """frame [B,1,S,S] (view of clip frames is fine: only the batch stride matters), action_norm [B,7] -> (cmds [B,5], params [B,6,1000])"""
         S = self.cfg.image_size

@@ -90,6 +90,9 @@ PROTOTYPES = {
     "vcad_wire_unpack": (_i, [_vp, _i64, _i64, _vp, _vp, _i, _vp]),
     "vcad_optimizer_step": (_i, [_vp, _f, _f, _f, _f, _f, _i, _f, _vp, _vp]),
     "vcad_optimizer_step_groups": (_i, [_vp, C.POINTER(_f), _f, _f, _f, _f, _i, _f, _vp, _vp]),
+    "vcad_set_input_grads": (_i, [_vp, _vp, _vp]),
+    "vcad_rollout_workspace_bytes": (_sz, [_vp, _i]),
+    "vcad_cad_attention_rollout": (_i, [_vp, _vp, _i, _vp, _vp]),
     "vcad_infer_workspace_bytes": (_sz, [_vp, _i, _i]),
     "vcad_infer_begin": (_i, [_vp, _vp, _i, _i, _vp]),
     "vcad_infer_begin_u8": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -111,6 +114,8 @@ PROTOTYPES = {
     "vcad_op_attention_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
                                    _i, _i, _i, _i, _i, _i, _f, _vp]),
     "vcad_op_cls_attention_fwd": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "vcad_op_patch_grad": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "vcad_op_attention_rollout": (_i, [_i, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "vcad_op_cls_attention_bwd": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _f, _vp]),
     "vcad_op_attention_bwd_o": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
                                      _i, _i, _i, _i, _i, _i, _f, _vp]),

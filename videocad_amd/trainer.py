@@ -792,6 +792,47 @@ class BaseTrainer:
             self.save_metrics(metrics, f"{mode}_epoch_{epoch + 1}" if epoch != -1 else mode)
         return metrics
 
+    # ---- interpretability maps (reference trainer.py:604-711): native pixel gradients and CAD-tower attention rollout
+    @staticmethod
+    def _float_pixels(x):
+        """uint8 grayscale pixels -> the normalised fp32 image the patchify kernel would have formed, (u / 255 - 0.5) / 0.5; fp32 unchanged"""
+        return (x.float() / 255.0 - 0.5) / 0.5 if x.dtype == torch.uint8 else x.float()
+
+    def generate_saliency_batch(self, dataloader, target_class=None):
+        """One batch of `dataloader`, first time step: |d cmd_logit[target] / d cad_image| maxed over the channel.  target_class None = the arg-max
+        command per sample.  Returns (cad_image [B, 1, S, S], saliency [B, S, S]).  Leaves the model in eval mode, as the reference does.
+        Deviation: with num_views > 0 every view is passed (the reference's [:, :1] slice does not fit embed_multiview's V-wide input)."""
+        self.model.eval()
+        bd = self.prepare_batch(next(iter(dataloader)))
+        cad = self._float_pixels(bd["cad_image"]).clone().detach().requires_grad_(True)
+        inputs = {"frames": self._float_pixels(bd["frames"][:, :1]), "actions": self.normalize_actions(bd["actions"][:, :1]),
+                  "timesteps": bd["timesteps"], "cad_image": cad}
+        if "multiview_images" in bd:
+            inputs["multiview_images"] = self._float_pixels(bd["multiview_images"])
+        with torch.enable_grad():
+            cmds, _ = self.model(inputs)
+            first = cmds[:, 0]
+            target = first.argmax(dim=1) if target_class is None else target_class
+            first[torch.arange(first.shape[0], device=first.device), target].sum().backward()
+        return cad.detach(), cad.grad.abs().amax(dim=1)
+
+    def compute_attention_rollout(self, input_batch, discard_ratio=0.0):
+        """Attention rollout of the CAD encoder: per layer the head-averaged attention plus identity, row-normalised, multiplied over the layers; the
+        class token's row over the patches, bilinearly upsampled to the image size.  Returns [B, S, S] on the CPU.  discard_ratio is accepted and
+        ignored, as in the reference.  Leaves the model in eval mode."""
+        self.model.eval()
+        native = self.native
+        if not native._shadow_fresh:
+            self.engine.sync_shadow()
+        native._shadow_fresh = False
+        cad = self._float_pixels(input_batch["cad_image"].to(self.device))
+        with torch.no_grad():
+            m = self.engine.attention_rollout(cad)
+            g = int(round(m.shape[1] ** 0.5))
+            S = self.engine.cfg.image_size
+            m = torch.nn.functional.interpolate(m.view(-1, 1, g, g), size=(S, S), mode="bilinear", align_corners=False)
+        return m.squeeze(1).cpu()
+
     def _predict_actions(self, model, inputs):
         cmds, pars = model(inputs)
         pred_cmd = torch.argmax(cmds, dim=-1)
